@@ -7,7 +7,11 @@ buffers, 1/2/4/8 GPU".
   B independent 1 MiB Silesia-style buffers (C4's per-GPU shard: 262144 / 8 =
   32768 buffers), inputs resident in HBM (generated on the device), outputs
   written to HBM.  `value` = total input MB (1e6 B) compressed by all ranks / max
-  elapsed over ranks.
+  elapsed over ranks.  `ms_per_step` = that elapsed time / --steps.
+* A plain run does only this: it sets up, warms up, times --steps steps, writes
+  the last step's outputs if --dump-outputs DIR is given (dump_outputs), and
+  prints the result line.  Everything below runs, and appears in the line, only
+  with --full.
 * CRC-32 leg (C2: 1 M x 4 KiB random buffers on each GPU) reported as "crc32".
 * roofline: the dominant deflate kernel (k_match) and the CRC kernel, timed
   live with HIP events on their launch stream; algorithmic bytes per SURVEY
@@ -105,7 +109,18 @@ def parse(argv=None):
                     help="test mode: gloo + oracle instead of the GPU legs (launcher/reduction check)")
     ap.add_argument("--plan-only", action="store_true",
                     help="print each rank's HBM / host memory plan for these arguments and exit (no compute)")
-    return ap.parse_args(argv)
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed deflate steps also run everything else this benchmark measures and "
+                         "checks: the inflate, CRC-32 and Adler-32 legs, the reference / oracle verification, "
+                         "the CPU baselines, the rooflines and the memory plan (off: only the headline figure)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed deflate step computed as DIR/<name>.npy (see dump_outputs)")
+    a = ap.parse_args(argv)
+    if a.steps < 1:
+        ap.error("--steps must be at least 1")
+    if a.warmup < 0:
+        ap.error("--warmup must not be negative")
+    return a
 
 
 # ------------------------------------------------------------------ launch
@@ -230,12 +245,16 @@ def deflate_leg(a, D):
     stages = zgpu.stage_timing_read()
     errors = int((st != 0).sum().item())
     out_bytes = int(dlen.sum().item())
-    # per-rank digest of the output: sum of stream lengths and XOR of stream CRCs
-    scrc = torch.zeros(B, dtype=torch.int32, device="cuda")
-    zgpu.crc32_batch_dev(dst, doff, dlen, scrc)
-    digest = _xor_all(scrc)
-    return dict(src=src, dst=dst, dlen=dlen, cap=cap, elapsed=el, stages=stages, errors=errors,
-                out_bytes=out_bytes, in_bytes=n * B, digest=digest, scrc=scrc, first=first)
+    return dict(src=src, dst=dst, doff=doff, dlen=dlen, st=st, cap=cap, elapsed=el, stages=stages, errors=errors,
+                out_bytes=out_bytes, in_bytes=n * B, first=first)
+
+
+def stream_crcs(d):
+    """CRC-32 of every stream the deflate leg wrote (computed on the device, once)."""
+    if "scrc" not in d:
+        d["scrc"] = torch.zeros(d["dlen"].numel(), dtype=torch.int32, device="cuda")
+        zgpu.crc32_batch_dev(d["dst"], d["doff"], d["dlen"], d["scrc"])
+    return d["scrc"]
 
 
 def shard_golden_check(a, D, d):
@@ -255,7 +274,7 @@ def shard_golden_check(a, D, d):
                                                          doc["level"]):
         return 0, False, "no golden for this configuration (kind, buffer size, buffers, level)"
     lens = d["dlen"].cpu().numpy().astype(np.uint64)
-    crcs = d["scrc"].cpu().numpy().view(np.uint32)
+    crcs = stream_crcs(d).cpu().numpy().view(np.uint32)
     checked, dig = 0, False
     r = str(D.rank)
     if r in doc["ranks"]:
@@ -354,14 +373,18 @@ def dry_deflate_leg(a, D):
     in_b = out_b = digest = 0
     for _ in range(a.steps):
         in_b = out_b = digest = 0
+        status, streams = [], []
         for g in range(first, last):
             data = o.generate(a.buffer_bytes, 1, KIND_ID[a.kind], 2025, g)[0]
-            z = o.compress(data, a.level)[1]
+            rc, z = o.compress(data, a.level)
             in_b += len(data)
             out_b += len(z)
             digest ^= _z.crc32(z)
+            status.append(rc)
+            streams.append(z)
     return dict(elapsed=time.perf_counter() - t0, in_bytes=in_b, out_bytes=out_b, errors=0,
-                digest=digest, stages={})
+                digest=digest, stages={}, status=status, streams=streams,
+                cap=(zgpu.compress_bound(a.buffer_bytes) + 15) // 16 * 16)
 
 
 def dry_digest_check(a, digests):
@@ -384,6 +407,70 @@ def dry_digest_check(a, digests):
         assert got == want, f"rank {r}: dry-run digest {got} != reference {want}"
         n += 1
     return n, f"reference {doc.get('reference')}"
+
+
+# ------------------------------------------------------------------ --dump-outputs
+
+DUMP_SAMPLE_VALUES = 10 << 20     # stream bytes kept, one float32 each: 42 MB of the 64 MB a dump may take
+DUMP_MAX_BUFFERS = 1 << 19        # buffers whose length / status / CRC are kept (28 B each with the index)
+
+
+def dump_outputs(a, D, d):
+    """--dump-outputs DIR: what the last timed deflate step left for its caller,
+    as float32 / float64 .npy files (under 64 MB in all), so that two builds run
+    with the same arguments -- which generate the same inputs -- can be compared
+    output for output.  Buffers are this rank's, in batch order:
+      stream_len     float64 [B]    length of every stream (dlen)
+      status         float32 [B]    zlib status of every buffer
+      stream_crc32   float64 [B]    CRC-32 of every stream's bytes: not an output of
+                                    the timed path, but the one figure here that
+                                    changes with any byte of any stream
+      sample_index   float64 [K]    the K buffers whose streams are kept whole (a
+                                    fixed seeded choice, ascending)
+      sample_streams float32 [K, W] their bytes, zero past each stream's end (W: the
+                                    output capacity of a buffer, at most 10 Mi)
+    With more than 2^19 buffers the three per-buffer arrays hold a seeded choice
+    of 2^19 of them, listed in buffer_index.npy.  A rank of a multi-GPU run adds
+    _rank<r> to the names."""
+    import numpy as np
+    B, cap = a.buffers, d["cap"]
+    if a.cpu_dry_run:
+        import zlib as _z
+        lens_i = np.array([len(z) for z in d["streams"]], dtype=np.int64)
+        status = np.array(d["status"], dtype=np.float32)
+        crcs = np.array([_z.crc32(z) for z in d["streams"]], dtype=np.float64)
+
+        def stream(i, w):
+            return np.frombuffer(d["streams"][i][:w], dtype=np.uint8)
+    else:
+        lens_i = d["dlen"].cpu().numpy()
+        status = d["st"].cpu().numpy().astype(np.float32)
+        crcs = stream_crcs(d).cpu().numpy().view(np.uint32).astype(np.float64)
+
+        def stream(i, w):
+            return d["dst"][i * cap: i * cap + min(int(lens_i[i]), w)].cpu().numpy()
+
+    out = {}
+    if B > DUMP_MAX_BUFFERS:
+        sel = np.sort(np.random.default_rng(2026).choice(B, DUMP_MAX_BUFFERS, replace=False))
+        out["buffer_index"] = sel.astype(np.float64)
+    else:
+        sel = np.arange(B)
+    out["stream_len"] = lens_i[sel].astype(np.float64)
+    out["status"] = status[sel]
+    out["stream_crc32"] = crcs[sel]
+    width = min(cap, DUMP_SAMPLE_VALUES)
+    idx = np.sort(np.random.default_rng(2025).choice(B, max(1, min(B, DUMP_SAMPLE_VALUES // width)), replace=False))
+    sample = np.zeros((idx.size, width), dtype=np.float32)
+    for k, i in enumerate(idx):
+        z = stream(int(i), width)
+        sample[k, :z.size] = z
+    out["sample_index"] = idx.astype(np.float64)
+    out["sample_streams"] = sample
+    os.makedirs(a.dump_outputs, exist_ok=True)
+    sfx = "" if D.world == 1 else f"_rank{D.rank}"
+    for name, arr in out.items():
+        np.save(os.path.join(a.dump_outputs, name + sfx + ".npy"), arr)
 
 
 # Device memory of one rank (bytes), from the library's allocations (DESIGN.md
@@ -695,24 +782,70 @@ def main(argv=None):
 
     if a.cpu_dry_run:
         d = dry_deflate_leg(a, D)
-        inf = c = ad = None
     else:
         assert zgpu.load().zgpu_init() == 0, "libzgpu: GPU init failed"
         zgpu.set_inflight_bytes(a.inflight_mb << 20)
         progress("deflate leg")
         d = deflate_leg(a, D)
-        progress("inflate leg")
-        inf = None if a.no_inflate else inflate_leg(a, D, d)
-        progress("checksum legs")
-        c = checksum_leg(a, D, "crc32")
-        ad = checksum_leg(a, D, "adler32") if a.adler_buffers > 0 else None
+    if a.dump_outputs:
+        dump_outputs(a, D, d)
 
     # ---- the end-of-run collectives (the only ones: no data-path exchange) ----
     el, = D.max(d["elapsed"])
     in_total, out_total, errors = D.sum(float(d["in_bytes"]) * a.steps, float(d["out_bytes"]),
                                         float(d["errors"]))
-    digests = D.gather([int(d["digest"]), int(d["out_bytes"])])
     assert errors == 0, f"deflate status != Z_OK on {int(errors)} buffers"
+    mbps = in_total / el / 1e6
+    more = full_report(a, D, d, mbps) if a.full else {}
+
+    if D.rank == 0:
+        line = {
+            "metric": METRIC,
+            "value": round(mbps, 1),
+            "unit": "MB/s",
+            "n_gpus": D.world,
+            "steps": a.steps,
+            "warmup": a.warmup,
+            "ms_per_step": round(el / a.steps * 1e3, 2),
+            "higher_is_better": True,
+            "scaling": "weak",
+            "vs_baseline": None,
+            "dtype": "u8",
+            "data": KIND_DATA[a.kind] if not a.cpu_dry_run else "cpu dry run: the generator's host twin (oracle/zgen.c), oracle",
+            "config": {"workload": f"{KIND_CONFIG[a.kind]}: {a.buffers} x {a.buffer_bytes} B buffers per GPU, "
+                                   f"deflate level {a.level}, zlib wrapper, inputs+outputs in HBM",
+                       "level": a.level, "buffer_bytes": a.buffer_bytes,
+                       "buffers_per_gpu": a.buffers, "inflight_mb": a.inflight_mb,
+                       "parallelism": f"{D.world} GPU(s), one rank each, buffers sharded by index, "
+                                      f"no data-path collective",
+                       "collective_backend": D.backend, "world_size_seen": D.world},
+            "compression_ratio": round(in_total / a.steps / max(1.0, out_total), 4),
+            "stage_ms_per_step": {k: round(v[0] / max(1, a.steps), 2) for k, v in d["stages"].items()},
+            "full": a.full,
+        }
+        line.update(more)
+        print(json.dumps(line), flush=True)
+    D.close()
+
+
+def full_report(a, D, d, mbps):
+    """--full: everything beyond the headline figure -- the inflate and checksum
+    legs, the per-rank digests, the verification against the compiled
+    reference's goldens and the oracle, the CPU baselines, the rooflines and the
+    memory plan.  Runs on every rank (it has collectives of its own) after the
+    timed deflate leg `d`; returns the keys it adds to the result line."""
+    if a.cpu_dry_run:
+        inf = c = ad = None
+        digest = d["digest"]
+    else:
+        progress("inflate leg")
+        inf = None if a.no_inflate else inflate_leg(a, D, d)
+        progress("checksum legs")
+        c = checksum_leg(a, D, "crc32")
+        ad = checksum_leg(a, D, "adler32") if a.adler_buffers > 0 else None
+        # per-rank digest of the output: sum of stream lengths and XOR of stream CRCs
+        digest = _xor_all(stream_crcs(d))
+    digests = D.gather([int(digest), int(d["out_bytes"])])
 
     # ---- verification on this rank (outside the timed region) ----
     if a.cpu_dry_run:
@@ -756,8 +889,6 @@ def main(argv=None):
                                                   checksum_cpu_baseline(a, "adler32", ad) if cpu_on else None)
 
     if D.rank == 0:
-        mbps = in_total / el / 1e6
-        ratio = in_total / a.steps / max(1.0, out_total)
         st = d["stages"]
         roof = None
         # dominant kernel: k_match ("match") at L4-9, k_parse_fast ("parse_greedy")
@@ -796,29 +927,8 @@ def main(argv=None):
                                        "vs_one_core": round(mbps / cpu["per_core_1thread"], 1),
                                        "vs_all_host_cpus_linear_estimate":
                                            round(mbps / cpu["all_host_cpus_linear_estimate"], 3)}
-        line = {
-            "metric": METRIC,
-            "value": round(mbps, 1),
-            "unit": "MB/s",
-            "n_gpus": D.world,
-            "steps": a.steps,
-            "warmup": a.warmup,
-            "ms_per_step": round(el / a.steps * 1e3, 2),
-            "higher_is_better": True,
-            "scaling": "weak",
-            "vs_baseline": None,
-            "dtype": "u8",
-            "data": KIND_DATA[a.kind] if not a.cpu_dry_run else "cpu dry run: the generator's host twin (oracle/zgen.c), oracle",
-            "config": {"workload": f"{KIND_CONFIG[a.kind]}: {a.buffers} x {a.buffer_bytes} B buffers per GPU, "
-                                   f"deflate level {a.level}, zlib wrapper, inputs+outputs in HBM",
-                       "level": a.level, "buffer_bytes": a.buffer_bytes,
-                       "buffers_per_gpu": a.buffers, "inflight_mb": a.inflight_mb,
-                       "parallelism": f"{D.world} GPU(s), one rank each, buffers sharded by index, "
-                                      f"no data-path collective",
-                       "collective_backend": D.backend, "world_size_seen": D.world},
-            "compression_ratio": round(ratio, 4),
+        return {
             "roofline": roof,
-            "stage_ms_per_step": {k: round(v[0] / max(1, a.steps), 2) for k, v in st.items()},
             "crc32": None if crc is None else dict(crc, workload=f"C2: {a.crc_buffers} x {a.crc_bytes} B "
                                                                  f"uniform random per GPU"),
             "adler32": None if adl is None else dict(adl, workload=f"C5 shape: {a.adler_buffers} x "
@@ -847,8 +957,7 @@ def main(argv=None):
             "cpu_baseline": cpu,
             "memory_plan": memory_plan(a, D.world),
         }
-        print(json.dumps(line), flush=True)
-    D.close()
+    return {}
 
 
 if __name__ == "__main__":

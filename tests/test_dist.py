@@ -96,7 +96,7 @@ def test_bench_gpus_flag_launches_ranks():
     env = {k: v for k, v in os.environ.items()
            if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
     per_gpu, nbytes = 3, 20000
-    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--cpu-dry-run",
+    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--cpu-dry-run", "--full",
                         "--buffers", str(per_gpu), "--buffer-bytes", str(nbytes), "--steps", "1",
                         "--warmup", "0"], capture_output=True, text=True, timeout=300, env=env, cwd="/tmp")
     assert r.returncode == 0, r.stderr[-2000:]
@@ -143,7 +143,7 @@ def test_bench_world8_dry_run_matches_reference_digests():
     env = {k: v for k, v in os.environ.items()
            if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
     env["OMP_NUM_THREADS"] = "1"
-    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "8", "--cpu-dry-run",
+    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "8", "--cpu-dry-run", "--full",
                         "--buffers", str(g["buffers_per_rank"]), "--buffer-bytes", str(g["buffer_bytes"]),
                         "--steps", "1", "--warmup", "0"], capture_output=True, text=True, timeout=600, env=env,
                        cwd="/tmp")
@@ -186,3 +186,46 @@ def test_bench_memory_plan_per_rank():
     assert p["hbm_fits"] is True and p["hbm_need_per_rank"] <= 288e9
     assert p["host_need_all_ranks_est"] == 8 * p["host_bytes_per_rank_est"]
     assert plan("--inflight-mb", "8192")["hbm_fits"] is False
+
+
+def test_bench_plain_run_is_lean_and_dumps_outputs(tmp_path, capsys):
+    """A plain `bench.py` run (no --full) reports the headline figure only, and
+    `--dump-outputs DIR` writes what the last timed step computed as float32 /
+    float64 .npy files that are identical from run to run and equal to the
+    oracle's streams for the same generated buffers (dry run: 3 x 20000 B)."""
+    import json
+    import zlib
+    import numpy as np
+    import bench
+    from zhelpers import Oracle
+    per_gpu, nbytes = 3, 20000
+    lines, dumps = [], []
+    for k in range(2):
+        out = tmp_path / f"dump{k}"
+        bench.main(["--gpus", "1", "--cpu-dry-run", "--buffers", str(per_gpu), "--buffer-bytes", str(nbytes),
+                    "--steps", "2", "--warmup", "0", "--dump-outputs", str(out)])
+        lines.append(json.loads([s for s in capsys.readouterr().out.splitlines() if s.startswith("{")][-1]))
+        dumps.append({p.stem: np.load(p, allow_pickle=False) for p in sorted(out.iterdir())})
+    line = lines[0]
+    assert line["full"] is False and line["steps"] == 2 and line["ms_per_step"] >= 0 and line["value"] > 0
+    for key in ("metric", "unit", "higher_is_better", "dtype", "compression_ratio"):
+        assert key in line
+    for key in ("cpu_baseline", "crc32", "adler32", "inflate", "roofline", "verified", "per_rank", "memory_plan"):
+        assert key not in line, key
+    a, b = dumps
+    assert sorted(a) == ["sample_index", "sample_streams", "status", "stream_crc32", "stream_len"]
+    assert sum(v.nbytes for v in a.values()) <= 64e6
+    for name in a:
+        assert a[name].dtype in (np.float32, np.float64), name
+        assert a[name].shape == b[name].shape and np.array_equal(a[name], b[name]), name
+    o = Oracle()
+    want = [o.compress(o.generate(nbytes, 1, 1, 2025, g)[0], 6)[1] for g in range(per_gpu)]
+    assert a["stream_len"].tolist() == [len(z) for z in want]
+    assert a["status"].tolist() == [0.0] * per_gpu
+    assert a["stream_crc32"].tolist() == [zlib.crc32(z) for z in want]
+    assert a["sample_index"].tolist() == list(range(per_gpu))
+    cap = (nbytes + (nbytes >> 12) + (nbytes >> 14) + (nbytes >> 25) + 13 + 15) // 16 * 16
+    assert a["sample_streams"].shape == (per_gpu, cap)
+    for row, z in zip(a["sample_streams"], want):
+        assert bytes(row[:len(z)].astype(np.uint8)) == z and not row[len(z):].any()
+    assert abs(line["compression_ratio"] - per_gpu * nbytes / sum(map(len, want))) < 1e-3

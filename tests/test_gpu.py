@@ -785,7 +785,7 @@ def test_bench_rccl_path_one_rank():
     s.close()
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node=1",
            "--master-addr=127.0.0.1", f"--master-port={port}", os.path.join(root, "bench.py"), "--gpus", "1",
-           "--steps", "1", "--warmup", "0", "--buffers", "64", "--no-cpu", "--no-inflate", "--crc-buffers", "4096",
+           "--full", "--steps", "1", "--warmup", "0", "--buffers", "64", "--no-cpu", "--no-inflate", "--crc-buffers", "4096",
            "--adler-buffers", "0", "--verify", "4"]
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=240, env=env, cwd=root)
     assert r.returncode == 0, r.stderr[-3000:]
@@ -793,3 +793,43 @@ def test_bench_rccl_path_one_rank():
     assert line["config"]["collective_backend"] == "nccl" and line["config"]["world_size_seen"] == 1
     assert line["n_gpus"] == 1 and line["value"] > 0
     assert len(line["per_rank"]) == 1 and line["per_rank"][0]["out_bytes"] > 0
+
+
+def test_bench_plain_run_dumps_last_step_outputs(zg, oracle, tmp_path):
+    """A plain `bench.py --gpus 1` run (no --full) on the GPU: the line holds the
+    headline figure and none of the --full legs, and --dump-outputs writes what
+    the last timed step left -- every stream's length, status and CRC-32, and a
+    seeded choice of whole streams -- equal to the oracle's streams for the
+    buffers the generator's host twin makes (48 x 256 KiB, two sub-batches)."""
+    import json
+    import subprocess
+    import sys
+    n, B = 1 << 18, 48
+    env = {k: v for k, v in os.environ.items()
+           if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1",
+           "--buffers", str(B), "--buffer-bytes", str(n), "--inflight-mb", "8", "--dump-outputs", str(tmp_path)]
+    r = subprocess.run(cmd, capture_output=True, text=True, timeout=240, env=env, cwd=ROOT)
+    assert r.returncode == 0, r.stderr[-3000:]
+    line = json.loads([x for x in r.stdout.splitlines() if x.startswith("{")][-1])
+    assert line["full"] is False and line["steps"] == 2 and line["n_gpus"] == 1
+    assert line["value"] > 0 and line["ms_per_step"] > 0 and line["unit"] == "MB/s" and line["dtype"] == "u8"
+    assert abs(line["value"] - n * B / 1e6 / (line["ms_per_step"] / 1e3)) <= 0.02 * line["value"]
+    for key in ("cpu_baseline", "crc32", "adler32", "inflate", "roofline", "verified", "per_rank", "memory_plan"):
+        assert key not in line, key
+    got = {p.stem: np.load(p, allow_pickle=False) for p in sorted(tmp_path.iterdir())}
+    assert sorted(got) == ["sample_index", "sample_streams", "status", "stream_crc32", "stream_len"]
+    assert all(v.dtype in (np.float32, np.float64) for v in got.values())
+    assert sum(v.nbytes for v in got.values()) <= 64e6
+    want = [oracle.compress(b, 6)[1] for b in oracle.generate(n, B, zg.KIND_SILESIA, 2025, 0)]
+    assert got["stream_len"].tolist() == [len(z) for z in want]
+    assert got["status"].tolist() == [0.0] * B
+    assert got["stream_crc32"].tolist() == [pyzlib.crc32(z) for z in want]
+    idx = [int(i) for i in got["sample_index"]]
+    cap = (zg.compress_bound(n) + 15) // 16 * 16
+    assert got["sample_streams"].shape == (len(idx), cap)
+    assert len(idx) == min(B, (10 << 20) // cap) and idx == sorted(set(idx)) and 0 <= idx[0] and idx[-1] < B
+    for row, i in zip(got["sample_streams"], idx):
+        z = want[i]
+        assert bytes(row[:len(z)].astype(np.uint8)) == z and not row[len(z):].any(), i
+    assert abs(line["compression_ratio"] - n * B / sum(map(len, want))) < 1e-3
